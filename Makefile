@@ -19,7 +19,7 @@ sanitize:         ## ASan/UBSan + TSan self-test of the native host code
 	$(PY) -m pytest tests/test_native_sanitizers.py -q
 
 bench: build      ## headline: BASELINE config 2 (MB/s staged + p50 latency)
-	$(PY) bench.py --steps 16 --warmup 2 --compare-reference
+	$(PY) bench.py --steps 16 --warmup 2 --full --compare-reference
 
 bench-configs: build
 	$(PY) -m downloader_amd.bench.configs --config 1 --config 3 --config 4 --config 5

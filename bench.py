@@ -31,12 +31,24 @@ re-reading every byte on the worker's CPUs - and (c) with ``--sink sample`` (def
 windows / every byte) with zero mismatches. The origin's bytes repeat with a period of
 64 MiB + 4 KiB, so a part or piece fetched from the wrong offset never matches.
 
-Same-call extras of the line: ``unchecked_MBps`` (``s3.checksum: auto``: the plain relay
+A plain run does only what the headline needs: peers and workers up, warmup, the timed steps,
+the sink checks above, the result line. ``--full`` adds the same-call extras of the line (each
+with its own ``--no-...`` switch): ``unchecked_MBps`` (``s3.checksum: auto``: the plain relay
 spliced with no payload checksum), ``reference_mode_MBps`` (reference-equivalent mode,
 BASELINE.md: one serial prefetch-1 consumer per process, ``--ref-procs`` of them, on the same
-CPUs; ``vs_baseline`` = headline / it), ``workers_curve`` (MB/s and p50 at 1/2/4/8 worker
-processes of the rank), config 1's p50 (a single 10 MB job, tuned and reference mode) and the
-streamed-torrent GPU vs host A/B.
+CPUs; ``vs_baseline`` = headline / it, null without it), ``workers_curve`` (MB/s and p50 at
+1/2/4/8 worker processes of the rank), config 1's p50 (a single 10 MB job, tuned and reference
+mode), ``--compare-single-put`` and the streamed-torrent GPU vs host A/B.
+
+``--dump-outputs DIR`` writes what the last timed step handed back, one row per job of that
+step in (worker process, job number) order, as float64 ``DIR/<name>.npy``: ``jobs`` (worker
+id, job number), ``staged`` (1.0 = the worker reported the job staged), ``staged_bytes`` (the
+bytes the worker says it uploaded) and ``object_bytes`` (the size the S3 peer holds under the
+job's object key, -1 when it has none); and ``sink_checks``, the S3 peer's verdict on all
+timed objects (objects matched against the origin's bytes, mismatches, objects it could not
+match to an origin request, bodies refused for a wrong checksum). Job names, sizes and origin
+seeds depend on the arguments only, so two builds run with the same arguments give comparable
+files.
 """
 from __future__ import annotations
 
@@ -64,6 +76,13 @@ def parse() -> argparse.Namespace:
     p.add_argument("--gpus", type=int, default=1, help="worker processes (one per GPU slot)")
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also run the same-call extras of the line: unchecked relay, reference "
+                        "mode (vs_baseline), workers curve, config 1, --compare-single-put and "
+                        "the torrent GPU vs host A/B (each still has its own --no-... switch)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write the last step's per-job results (worker's "
+                        "outcome and byte count, object size held by the S3 peer) as DIR/*.npy")
     p.add_argument("--size-mb", type=float, default=100.0, help="object size in MB (1e6 B)")
     p.add_argument("--mode", choices=["tuned", "reference"], default="tuned")
     p.add_argument("--concurrency", type=int, default=4,
@@ -141,7 +160,13 @@ def parse() -> argparse.Namespace:
                    help="skip the same-call config 1 (single 10 MB job) p50, tuned and reference")
     p.add_argument("--curve-warmup-jobs", type=int, default=8,
                    help="untimed jobs per worker process before each curve point")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:        # a plain run measures the headline only
+        args.compare_unchecked = args.compare_single_put = args.compare_reference = False
+        args.config1 = False
+        args.workers_curve = ""
+        args.torrent_gb = 0.0
+    return args
 
 
 @contextlib.contextmanager
@@ -324,7 +349,67 @@ async def _timed(args, worker, url, wid: int, mode: str, count: int) -> dict:
             "err": bad[0].error if bad else "", "loop_busy": loop_cpu / max(1e-9, t1 - t0),
             "cpu_s": cpu1 - cpu0, "sys_s": sys1 - sys0,
             "relay": {k: rc1[k] - rc0.get(k, 0) for k in rc1},
-            "pipes_created": pipes.get("created", 0), "pipes_short": pipes.get("short", 0)}
+            "pipes_created": pipes.get("created", 0), "pipes_short": pipes.get("short", 0),
+            "last_step": _last_step(args, wid, res, count)}
+
+
+def _last_step(args, wid: int, res, count: int) -> list:
+    """What this worker process' share of the last timed step handed back (--dump-outputs):
+    (worker id, job number, staged, bytes) of its timed jobs k with k * steps // count ==
+    steps - 1, by job number."""
+    if not getattr(args, "dump_outputs", ""):
+        return []
+    first = _warmup_jobs(args)
+    rows = []
+    for r in res:
+        i = int(r.job_id.rsplit("-j", 1)[1])
+        if (i - first) * args.steps // max(1, count) == args.steps - 1:
+            rows.append((wid, i, 1.0 if r.outcome == "staged" else 0.0, float(r.bytes)))
+    return sorted(rows)
+
+
+def _object_sizes(args, endpoint: str, mode: str, rows: list) -> list:
+    """The size the S3 peer holds under each row's object key (HEAD; -1: no such object)."""
+    import http.client
+    from downloader_amd.models import keys
+    from downloader_amd.utils.config import S3Config
+    from urllib.parse import quote
+    bucket = S3Config().bucket
+    host, port = endpoint.split(":")
+    ctx = None
+    if args.tls != "off":
+        import ssl
+        ctx = ssl.create_default_context(cafile=args.ca_file)
+    out = []
+    for wid, i, _, _ in rows:
+        key = keys.object_key(f"bench-{_tag(args, mode)}-r{wid}-j{i}", f"r{wid}-j{i}.mkv")
+        conn = (http.client.HTTPSConnection(host, int(port), timeout=30, context=ctx) if ctx
+                else http.client.HTTPConnection(host, int(port), timeout=30))
+        try:
+            conn.request("HEAD", f"/{bucket}/" + quote(key, safe="/"))
+            r = conn.getresponse()
+            r.read()
+            out.append(float(r.getheader("Content-Length", "-1")) if r.status == 200 else -1.0)
+        finally:
+            conn.close()
+    return out
+
+
+SINK_CHECK_KEYS = ("verify_objects", "mismatches_total", "unknown_total", "bad_digests_total")
+
+
+def dump_outputs(directory: str, rows: list, sink: dict) -> None:
+    """--dump-outputs: one row per job of the last timed step, float64 .npy files; plus the S3
+    peer's verdict on the timed objects (SINK_CHECK_KEYS, in that order)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "sink_checks.npy"),
+            np.asarray([sink[k] for k in SINK_CHECK_KEYS], dtype=np.float64))
+    a = np.asarray(rows, dtype=np.float64).reshape(-1, 5)
+    np.save(os.path.join(directory, "jobs.npy"), a[:, 0:2])
+    np.save(os.path.join(directory, "staged.npy"), a[:, 2])
+    np.save(os.path.join(directory, "staged_bytes.npy"), a[:, 3])
+    np.save(os.path.join(directory, "object_bytes.npy"), a[:, 4])
 
 
 def _relay_counters() -> dict:
@@ -480,7 +565,8 @@ def rank_procs(args, dist: Dist, endpoint: str, mode: str, stage_root: str, npro
             "pipes_short": sum(o["pipes_short"] for o in outs),
             "cpu_s": cpu1 - cpu0 + sum(o["cpu_s"] for o in outs),
             "sys_s": sys1 - sys0 + sum(o["sys_s"] for o in outs),
-            "relay": _sum_dicts(o["relay"] for o in outs)}
+            "relay": _sum_dicts(o["relay"] for o in outs),
+            "last_step": sorted(x for o in outs for x in o["last_step"])}
 
 
 SINK_KEYS = ("bytes_received", "verify_objects", "verify_bytes", "verify_mismatches",
@@ -528,6 +614,9 @@ def measure(args, dist: Dist, endpoint: str, mode: str, blob=None, nproc: int = 
     out["sink"]["mismatches_total"] = int(end.get("verify_mismatches", 0))
     out["sink"]["unknown_total"] = int(end.get("verify_unknown", 0))
     out["sink"]["bad_digests_total"] = int(end.get("bad_digests", 0))
+    if out["last_step"]:     # --dump-outputs: what the S3 peer holds for the last step's jobs
+        sizes = _object_sizes(args, endpoint, mode, out["last_step"])
+        out["last_step"] = [r + (s,) for r, s in zip(out["last_step"], sizes)]
     allr = dist.gather(out)
     elapsed = max(r["elapsed"] for r in allr)
     total_bytes = sum(r["bytes"] for r in allr)
@@ -574,7 +663,8 @@ def measure(args, dist: Dist, endpoint: str, mode: str, blob=None, nproc: int = 
             "breakdown": relay_breakdown(relay, worker_cpu, gb_all),
             "loop_busy": max(r["loop_busy"] for r in allr),
             "pipes_created": sum(r["pipes_created"] for r in allr),
-            "pipes_short": sum(r["pipes_short"] for r in allr)}
+            "pipes_short": sum(r["pipes_short"] for r in allr),
+            "last_step": sorted(tuple(x) for r in allr for x in r["last_step"])}
 
 
 def torrent_measure(args, dist: Dist) -> dict:
@@ -775,6 +865,10 @@ def main() -> int:
     tuned_mode = args.mode == "tuned"
     try:
         tuned = measure(args, dist, endpoint, args.mode, blob, nproc, pinned)
+        if args.dump_outputs:
+            if dist.rank == 0:
+                dump_outputs(args.dump_outputs, tuned["last_step"], tuned["sink"])
+            args.dump_outputs = ""       # the headline's outputs only, not the extras'
         unchecked = single = ref = tor = None
         cfg1: dict = {}
         curve = []

@@ -93,7 +93,7 @@ def test_bench_contract_two_ranks_gloo(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--size-mb", "4", "--jobs-per-step", "2",
-           "--torrent-gb", "0.05", "--torrent-pairs", "1", "--ref-jobs", "16",
+           "--full", "--torrent-gb", "0.05", "--torrent-pairs", "1", "--ref-jobs", "16",
            "--curve-steps", "1"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -115,7 +115,7 @@ def test_bench_contract_two_ranks_gloo(tmp_path):
 def test_bench_single_rank_defaults_are_valid(tmp_path):
     env = dict(os.environ, PYTHONPATH=REPO, LOG_LEVEL="error")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2",
-                        "--warmup", "1", "--size-mb", "2", "--torrent-gb", "0.2",
+                        "--warmup", "1", "--size-mb", "2", "--full", "--torrent-gb", "0.2",
                         "--torrent-pairs", "1", "--curve-steps", "1"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -149,6 +149,47 @@ def test_bench_single_rank_defaults_are_valid(tmp_path):
     assert j["gpu_host_fallbacks"] == 0
 
 
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """Without --full the line carries the headline and none of the same-call extras, and
+    --dump-outputs writes one float64 row per job of the last timed step (2 worker processes
+    x 3 steps x 4 jobs: the last 4 jobs), the same from run to run."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=REPO, LOG_LEVEL="error")
+    got = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+                            "--steps", "3", "--warmup", "1", "--jobs-per-step", "4",
+                            "--size-mb", "3", "--procs-per-rank", "2",
+                            "--dump-outputs", str(tmp_path / d)],
+                           env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.strip().splitlines()
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["config"]["jobs_timed"] == 12 and j["value"] > 0
+        assert j["ms_per_step"] > 0 and j["dtype"] == "bytes" and j["unit"] == "MB/s"
+        assert j["vs_baseline"] is None
+        for k in ("unchecked_MBps", "reference_mode_MBps", "workers_curve", "config1_p50_s",
+                  "config1_error", "single_put_MBps", "torrent_gpu_MBps", "torrent_error"):
+            assert k not in j, k
+        arrs = {n: np.load(tmp_path / d / f"{n}.npy")
+                for n in ("jobs", "staged", "staged_bytes", "object_bytes", "sink_checks")}
+        assert sorted(os.listdir(tmp_path / d)) == sorted(f"{n}.npy" for n in arrs)
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        got.append(arrs)
+    a = got[0]
+    # worker ids 0 and 1, each one's last step = its timed jobs 4 and 5 of 6 (job numbers 8
+    # and 9 after 4 warmup jobs)
+    assert a["jobs"].tolist() == [[0, 8], [0, 9], [1, 8], [1, 9]]
+    assert a["staged"].tolist() == [1.0] * 4
+    assert a["staged_bytes"].tolist() == [3_000_000.0] * 4
+    assert a["object_bytes"].tolist() == [3_000_000.0] * 4
+    # the S3 peer matched all 12 timed objects against the origin's bytes and refused nothing
+    assert a["sink_checks"].tolist() == [12.0, 0.0, 0.0, 0.0]
+    for n in a:
+        assert np.array_equal(a[n], got[1][n]), n
+
+
 def test_supervisor_auto_pinning_quota_share():
     from downloader_amd.parallel.supervisor import auto_cpus_per_worker, cpu_slices
     mask = list(range(256))
@@ -166,7 +207,7 @@ def test_bench_torrent_ab_failure_never_costs_the_headline(tmp_path):
     the line still prints, with the headline and the error."""
     env = dict(os.environ, PYTHONPATH=REPO, LOG_LEVEL="error")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1",
-                        "--warmup", "0", "--size-mb", "2", "--no-compare-single-put",
+                        "--warmup", "0", "--size-mb", "2", "--full", "--no-compare-single-put",
                         "--no-compare-crc", "--no-compare-reference", "--workers-curve", "",
                         "--torrent-gb", "0.2", "--torrent-timeout", "0.001"],
                        env=env, capture_output=True, text=True, timeout=300)
@@ -248,7 +289,7 @@ def test_bench_rank_with_two_worker_processes(tmp_path):
     env = dict(os.environ, PYTHONPATH=REPO, LOG_LEVEL="error")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2",
                         "--warmup", "1", "--jobs-per-step", "3", "--size-mb", "4",
-                        "--procs-per-rank", "2", "--torrent-gb", "0", "--compare-single-put",
+                        "--procs-per-rank", "2", "--full", "--torrent-gb", "0", "--compare-single-put",
                         "--no-compare-reference", "--workers-curve", ""],
                        env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
