@@ -54,12 +54,19 @@
 
 namespace py = pybind11;
 
+// A failed call also stays behind as the thread's "last error" until hipGetLastError() reads
+// it - later successful calls do not clear it - and every launch here is checked with
+// hipGetLastError(): an error that was already thrown (a PartHasher whose arena did not fit,
+// say) came back from the thread's next launch, which had nothing wrong with it. So the error
+// is taken off the thread as it is reported.
 #define HIP_CHECK(x)                                                                      \
   do {                                                                                    \
     hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess)                                                                 \
+    if (e_ != hipSuccess) {                                                               \
+      (void)hipGetLastError();                                                            \
       throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e_) + " at " + \
                                #x);                                                       \
+    }                                                                                     \
   } while (0)
 
 namespace {
@@ -1034,6 +1041,61 @@ class GpuVerifier {
     return {t[0] / iters, t[1] / iters, a == b ? 1.0 : 0.0};
   }
 
+  // Test entry: ONE launch of a PartHasher kernel on an exact lane table, so the tests can put
+  // any (offset, length) per lane against hashlib - in the PartHasher which lanes share a launch
+  // depends on arrival timing. `data` goes into a device buffer of n_bytes + kArenaPad whose pad
+  // holds 0xA5 (a tail that is not masked shows), the table is uploaded as the PartHasher lays
+  // it out (offsets, then lengths) and the grid / block are those of HipPartDevice::launch.
+  // kernel: 0 sha1_lanes_split_t<true>, 1 sha1_lanes_split_t<false>, 2 sha1_lanes<16>,
+  // 3 sha1_lanes<1>. Everything is checked here, before any device call: a lane outside `data`
+  // or, for the 16-byte-load kernels, off 16 bytes is refused (std::invalid_argument).
+  std::string hash_lanes(const uint8_t* p, int64_t n_bytes, const std::vector<int64_t>& off,
+                         const std::vector<int64_t>& len, int kernel) {
+    if (kernel < 0 || kernel > 3) throw std::invalid_argument("hash_lanes: unknown kernel");
+    if (off.empty() || off.size() != len.size() || off.size() > ((size_t)1 << 24))
+      throw std::invalid_argument("hash_lanes: need 1 .. 2^24 lanes, one length per offset");
+    if (n_bytes < 0) throw std::invalid_argument("hash_lanes: bad buffer");
+    const int n = (int)off.size();
+    for (int i = 0; i < n; ++i) {
+      const int64_t o = off[(size_t)i], l = len[(size_t)i];
+      if (o < 0 || l < 0 || o > n_bytes || l > n_bytes - o)
+        throw std::invalid_argument("hash_lanes: lane " + std::to_string(i) + " outside the data");
+      if (kernel != 3 && o % 16)
+        throw std::invalid_argument("hash_lanes: lane " + std::to_string(i) +
+                                    " is not 16-byte aligned");
+    }
+    HIP_CHECK(hipSetDevice(device_));
+    DevMem<uint8_t> data_buf((size_t)n_bytes + kArenaPad), out_buf((size_t)n * 20);
+    DevMem<int64_t> tab((size_t)n * 2);
+    std::vector<int64_t> h(off);
+    h.insert(h.end(), len.begin(), len.end());
+    std::string out((size_t)n * 20, '\0');
+    hipStream_t st = stream_[0];
+    HIP_CHECK(hipMemsetAsync(data_buf.p, 0xA5, (size_t)n_bytes + kArenaPad, st));
+    if (n_bytes) HIP_CHECK(hipMemcpyAsync(data_buf.p, p, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(tab.p, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(out_buf.p, 0, (size_t)n * 20, st));
+    const int64_t* dp = tab.p;
+    const int64_t* dl = tab.p + n;
+    const int block = 64, grid = (n + block - 1) / block;
+    if (kernel == 0)
+      hipLaunchKernelGGL(sha1_lanes_split_t<true>, dim3(grid), dim3(kSplitThreads), 0, st,
+                         data_buf.p, dp, dl, n, out_buf.p);
+    else if (kernel == 1)
+      hipLaunchKernelGGL(sha1_lanes_split_t<false>, dim3(grid), dim3(kSplitThreads), 0, st,
+                         data_buf.p, dp, dl, n, out_buf.p);
+    else if (kernel == 2)
+      hipLaunchKernelGGL(sha1_lanes<16>, dim3(grid), dim3(block), 0, st, data_buf.p, dp, dl, n,
+                         out_buf.p);
+    else
+      hipLaunchKernelGGL(sha1_lanes<1>, dim3(grid), dim3(block), 0, st, data_buf.p, dp, dl, n,
+                         out_buf.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(&out[0], out_buf.p, out.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return out;
+  }
+
   // Two sha1_lanes_split launches at once on the two streams (as the PartHasher's compute
   // streams run them), n0 and n1 lanes, against the first alone: (ms alone, ms stream 0, ms
   // stream 1), means over `iters` rounds. mode 1: stream 1 copies 48 x 64 MiB host -> device
@@ -1357,12 +1419,15 @@ class HipPartDevice {
     for (auto c : copies_) hipStreamSynchronize(c);
   }
   int reg(void* p, size_t n) {
-    if (hipSetDevice(device_) != hipSuccess) return -1;
-    return hipHostRegister(p, n, hipHostRegisterDefault) == hipSuccess ? 0 : -1;
+    if (hipSetDevice(device_) == hipSuccess &&
+        hipHostRegister(p, n, hipHostRegisterDefault) == hipSuccess)
+      return 0;
+    (void)hipGetLastError();         // reported as -1: not left for the thread's next launch
+    return -1;
   }
   void unreg(void* p) {
     hipSetDevice(device_);
-    hipHostUnregister(p);
+    if (hipHostUnregister(p) != hipSuccess) (void)hipGetLastError();
   }
 
  private:
@@ -1507,7 +1572,10 @@ py::dict part_stats(PartHasher& h) {
 
 int device_count() {
   int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
   return n;
 }
 
@@ -1646,6 +1714,30 @@ PYBIND11_MODULE(_gpuhash, m) {
           py::arg("piece_len"), py::arg("n_pieces"), py::arg("iters") = 3, py::arg("dup") = true,
           "(ms_split, ms_lanes, digests_equal): the PartHasher's two kernels on one lane table "
           "(dup=False: the split kernel with its idle lanes left idle)")
+      .def(
+          "hash_lanes",
+          [](GpuVerifier& g, const py::buffer& b, const std::vector<int64_t>& offsets,
+             const std::vector<int64_t>& lengths, const std::string& kernel) {
+            static const char* names[] = {"split", "split_idle", "lanes16", "lanes1"};
+            int k = -1;
+            for (int i = 0; i < 4; ++i)
+              if (kernel == names[i]) k = i;
+            if (k < 0)
+              throw std::invalid_argument("kernel must be split, split_idle, lanes16 or lanes1");
+            py::buffer_info info = b.request();
+            const int64_t n = (int64_t)info.size * (int64_t)info.itemsize;
+            std::string out;
+            {
+              py::gil_scoped_release rel;
+              out = g.hash_lanes((const uint8_t*)info.ptr, n, offsets, lengths, k);
+            }
+            return py::bytes(out);
+          },
+          py::arg("data"), py::arg("offsets"), py::arg("lengths"), py::arg("kernel"),
+          "Test entry: 20 digest bytes per lane from ONE launch of a PartHasher kernel (split = "
+          "sha1_lanes_split, split_idle = the same with idle lanes left idle, lanes16, lanes1) "
+          "over lanes (offsets[i], lengths[i]) of `data`; ValueError for a lane outside the data "
+          "or, except for lanes1, off 16 bytes")
       .def_property_readonly("batch_bytes", &GpuVerifier::batch_bytes);
   py::class_<PartHasher>(m, "PartHasher")
       .def(py::init([](int device, int64_t slot_bytes, int slots, int streams, int max_lanes,

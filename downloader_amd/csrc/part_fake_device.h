@@ -9,7 +9,9 @@
 //   * `lag`: probability that a completed copy still reads as not ready - the dispatcher then
 //     sees the slot's kernel finish before that copy, the order commit 363d26c had to handle;
 //   * `fail_launch_at` / `fail_query_at`: the Nth launch / event query throws, as a HIP error
-//     would (the hasher goes broken; parts it had finished must still be told).
+//     would (the hasher goes broken; parts it had finished must still be told);
+//   * a launch flagged align16 whose lanes are not all 16-byte aligned throws too: on the
+//     device that flag picks the dwordx4-load kernels over sha1_lanes<1>.
 #pragma once
 
 #include <atomic>
@@ -98,10 +100,19 @@ class FakePartDevice {
   }
   int64_t launch_lanes() const { return (int64_t)max_lanes_ * (int64_t)slots_.size(); }
   // One kernel over the lanes of several slots, in order (PartDispatcher's multi-slot launch).
+  // align16 is the dispatcher's promise that every lane of the launch starts on a 16-byte
+  // boundary (the HIP side then takes the dwordx4-load kernels): a launch that breaks it throws,
+  // as a device fault would, and the hasher goes broken.
   void launch(int stream, const int* slots, const int* lanes, int nslots, int total,
-              bool /*align16*/) {
+              bool align16) {
     if (k_.fail_launch_at && ++launches_ == k_.fail_launch_at)
       throw std::runtime_error("injected device fault (launch)");
+    if (align16)
+      for (int k = 0; k < nslots; ++k)
+        for (int l = 0; l < lanes[k]; ++l)
+          if (slots_[(size_t)slots[k]].lanes[(size_t)l] % 16)
+            throw std::runtime_error("align16 launch with a lane off 16 bytes");
+    (align16 ? launches_aligned_ : launches_unaligned_).fetch_add(1, std::memory_order_relaxed);
     Run* run = &runs_[(size_t)stream];
     run->done->store(0, std::memory_order_relaxed);
     std::vector<std::pair<Slot*, int>> group;
@@ -138,6 +149,9 @@ class FakePartDevice {
   void drain_copies() noexcept {
     for (auto& q : copies_) q->drain();
   }
+  // launches seen with align16 true / false (any thread)
+  int launches_aligned() const { return launches_aligned_.load(std::memory_order_relaxed); }
+  int launches_unaligned() const { return launches_unaligned_.load(std::memory_order_relaxed); }
   int reg(void*, size_t) { return 0; }
   void unreg(void*) {}
 
@@ -211,6 +225,7 @@ class FakePartDevice {
   FakeDeviceKnobs k_;
   std::mt19937 rng_;
   int launches_ = 0, queries_ = 0;
+  std::atomic<int> launches_aligned_{0}, launches_unaligned_{0};   // by the align16 they carried
   std::vector<Slot> slots_;
   std::vector<Run> runs_;
   std::vector<std::unique_ptr<Queue>> copies_, computes_;

@@ -817,8 +817,64 @@ static void multislot_section() {
   CHECK(st.lanes == (uint64_t)parts * pieces && st.pending == 0);
 }
 
+// The align16 flag of a launch (part_dispatch.h): ANDed over the launch's slots, it selects the
+// 16-byte-load kernels on the device, so it must be false whenever one lane is off 16 bytes.
+// Parts of 1000- and 999-byte pieces (lanes at 8- and 1-byte offsets) are interleaved with 16 KiB
+// ones from a few threads; the fake device throws on a flag that its lanes do not keep.
+static void align16_section() {
+  Watchdog wd("align16 launches", 60);
+  FakeDeviceKnobs k;
+  k.kernel_us_max = 3000;
+  k.copy_us_max = 100;
+  k.seed = 11;
+  auto h = fake_hasher(k);
+  const GpuPartHashApi* api = h->api();
+  const int64_t piece_of[3] = {1000, 999, 16384};
+  const int pieces = 8, threads = 4, parts = 24;
+  auto data = rnd((size_t)pieces * 16384 + 4096, 93);
+  std::atomic<bool> ok{true};
+  // one part: submitted, waited for, every piece against the host digest; the last piece is
+  // short for two parts in three
+  auto one = [&](int64_t piece, int idx) {
+    const int64_t len = pieces * piece - (idx % 3) * 5;
+    const uint8_t* p = data.data() + (idx * 37) % 4096;
+    uint64_t t = 0;
+    while (!(t = api->submit(api->ctx, p, len, piece)))
+      std::this_thread::sleep_for(std::chrono::microseconds(50));
+    uint8_t dig[pieces * 20];
+    char err[256] = {0};
+    if (api->wait(api->ctx, t, GPU_PART_DONE, dig, sizeof dig, err, sizeof err) != 0) {
+      fprintf(stderr, "align16: part of %lld-byte pieces failed: %s\n", (long long)piece, err);
+      ok = false;
+      return;
+    }
+    for (int q = 0; q < pieces; ++q) {
+      const int64_t po = q * piece, pl = std::min(piece, len - po);
+      if (digest("sha1", p + po, (size_t)pl) != std::string((const char*)dig + q * 20, 20)) ok = false;
+    }
+  };
+  // alone in their launches: one with the flag set and one without it, whatever the timing below
+  one(16384, 0);
+  one(1000, 1);
+  std::vector<std::thread> ths;
+  for (int t = 0; t < threads; ++t)
+    ths.emplace_back([&, t] {
+      for (int i = 0; i < parts; ++i) one(piece_of[(t + i) % 3], t * parts + i);
+    });
+  for (auto& th : ths) th.join();
+  const PartDispatchStats st = h->stats();
+  fprintf(stderr, "align16: %llu launches, %d with the flag, %d without\n",
+          (unsigned long long)st.launches, h->device().launches_aligned(),
+          h->device().launches_unaligned());
+  CHECK(ok.load());
+  CHECK(!st.broken && st.pending == 0);
+  CHECK(st.lanes == (uint64_t)(threads * parts + 2) * pieces);
+  CHECK(h->device().launches_aligned() >= 1 && h->device().launches_unaligned() >= 1);
+}
+
 static void stress_sections() {
   multislot_section();
+  align16_section();
   // ---- the completion machinery under load: 64 relays x 32 parts (2,048) through
   // PartDispatcher<FakePartDevice>, copies that complete before they are seen, hashers
   // replaced every few ms, the part budget oscillating, a third of the parts forgotten

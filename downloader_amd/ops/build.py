@@ -134,7 +134,8 @@ def build_selftest(kind: str, force: bool = False, verbose: bool = True) -> Path
     BIN.mkdir(exist_ok=True)
     out = BIN / f"selftest_{kind}"
     if force or _stale(out, srcs + [CSRC / "native.h", CSRC / "crc32c.h",
-                                    CSRC / "gpu_part_api.h", CSRC / "part_dispatch.h"]):
+                                    CSRC / "gpu_part_api.h", CSRC / "part_dispatch.h",
+                                    CSRC / "part_fake_device.h"]):
         cxx = os.environ.get("CXX", "g++")
         cmd = [cxx, "-O1", "-g", "-std=c++17", "-msse4.2", *SANITIZERS[kind],
                *[str(s) for s in srcs],
