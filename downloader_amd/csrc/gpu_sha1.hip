@@ -866,6 +866,9 @@ class GpuVerifier {
   // threads, pread from the page cache), copies it on the slot's stream and launches the
   // chunk kernel. Kernels are ordered across the two streams with events (state carries
   // over); the host refills a slot only after its previous copy completed.
+  // The chunk is min(chunk, piece_len) rounded down to whole blocks, at least 64 bytes and at
+  // most the staging slot (batch_bytes rounded down to 64): a larger `chunk` is clamped, not an
+  // error, and only a slot that cannot hold one block is grown - before any read or copy.
   // `which` (optional) restricts the check to those piece indices: the result then holds one
   // byte per listed piece, in list order (incremental verification of downloaded runs).
   std::vector<uint8_t> verify_files_streamed(
@@ -884,7 +887,11 @@ class GpuVerifier {
     std::vector<uint8_t> ok((size_t)np, 0);
     if (timing) *timing = {0.0, 0.0};
     if (np == 0) return ok;
-    const int64_t CH = std::max<int64_t>(64, std::min<int64_t>(chunk, piece_len) & ~(int64_t)63);
+    // One lane's chunk never exceeds a staging slot: with CH > batch_bytes_ the window was one
+    // lane (W = 1) whose CH bytes were pread into, and copied out of, slots of batch_bytes_.
+    int64_t CH = std::max<int64_t>(64, std::min<int64_t>(chunk, piece_len) & ~(int64_t)63);
+    if (batch_bytes_ < 64) grow(CH);   // no room for one block (0: an earlier grow() failed)
+    CH = std::min<int64_t>(CH, batch_bytes_ & ~(int64_t)63);
     const int64_t W = std::max<int64_t>(1, std::min<int64_t>(m, batch_bytes_ / CH));
     const int64_t last_len = fs.total - (np - 1) * piece_len;
     DevMem<uint8_t> exp_buf((size_t)np * 20), ok_buf((size_t)np);
@@ -1049,12 +1056,19 @@ class GpuVerifier {
   // kernel: 0 sha1_lanes_split_t<true>, 1 sha1_lanes_split_t<false>, 2 sha1_lanes<16>,
   // 3 sha1_lanes<1>. Everything is checked here, before any device call: a lane outside `data`
   // or, for the 16-byte-load kernels, off 16 bytes is refused (std::invalid_argument).
+  // `base` puts the table where the production arena has it (8 slots of 1 GiB: lane offsets of
+  // up to 8 GiB from the kernel's `data`): the device buffer is base + n_bytes + kArenaPad
+  // bytes, `data` sits at buf + base, lane i is uploaded as base + off[i], and only
+  // [base, base + n_bytes + kArenaPad) is written (0xA5, then `data`) - the gigabytes below it
+  // are never touched. base: a multiple of 256 (a part's alignment in its slot), 0 .. 8 GiB.
   std::string hash_lanes(const uint8_t* p, int64_t n_bytes, const std::vector<int64_t>& off,
-                         const std::vector<int64_t>& len, int kernel) {
+                         const std::vector<int64_t>& len, int kernel, int64_t base = 0) {
     if (kernel < 0 || kernel > 3) throw std::invalid_argument("hash_lanes: unknown kernel");
     if (off.empty() || off.size() != len.size() || off.size() > ((size_t)1 << 24))
       throw std::invalid_argument("hash_lanes: need 1 .. 2^24 lanes, one length per offset");
     if (n_bytes < 0) throw std::invalid_argument("hash_lanes: bad buffer");
+    if (base < 0 || base % 256 || base > ((int64_t)8 << 30))
+      throw std::invalid_argument("hash_lanes: base must be a multiple of 256 in 0 .. 8 GiB");
     const int n = (int)off.size();
     for (int i = 0; i < n; ++i) {
       const int64_t o = off[(size_t)i], l = len[(size_t)i];
@@ -1065,14 +1079,16 @@ class GpuVerifier {
                                     " is not 16-byte aligned");
     }
     HIP_CHECK(hipSetDevice(device_));
-    DevMem<uint8_t> data_buf((size_t)n_bytes + kArenaPad), out_buf((size_t)n * 20);
+    DevMem<uint8_t> data_buf((size_t)base + (size_t)n_bytes + kArenaPad), out_buf((size_t)n * 20);
     DevMem<int64_t> tab((size_t)n * 2);
     std::vector<int64_t> h(off);
+    for (int64_t& o : h) o += base;
     h.insert(h.end(), len.begin(), len.end());
     std::string out((size_t)n * 20, '\0');
     hipStream_t st = stream_[0];
-    HIP_CHECK(hipMemsetAsync(data_buf.p, 0xA5, (size_t)n_bytes + kArenaPad, st));
-    if (n_bytes) HIP_CHECK(hipMemcpyAsync(data_buf.p, p, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    uint8_t* at = data_buf.p + base;
+    HIP_CHECK(hipMemsetAsync(at, 0xA5, (size_t)n_bytes + kArenaPad, st));
+    if (n_bytes) HIP_CHECK(hipMemcpyAsync(at, p, (size_t)n_bytes, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(tab.p, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(out_buf.p, 0, (size_t)n * 20, st));
     const int64_t* dp = tab.p;
@@ -1090,6 +1106,43 @@ class GpuVerifier {
     else
       hipLaunchKernelGGL(sha1_lanes<1>, dim3(grid), dim3(block), 0, st, data_buf.p, dp, dl, n,
                          out_buf.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(&out[0], out_buf.p, out.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return out;
+  }
+
+  // Test entry: ONE launch of sha1_pieces<16, B3, PF> on `data` (pieces of piece_len, a
+  // shorter last one) and its digests, so the arms that only the kernel benches launch - and
+  // whose digests those throw away - meet hashlib too. variant: 0 <true, true> (what launch()
+  // uses), 1 <false, true> (plain C rounds), 2 <true, false> (no block prefetch). Checked
+  // before any device call (std::invalid_argument): 16 | piece_len, a known variant, 1 .. 2^24
+  // pieces.
+  std::string hash_pieces_variant(const uint8_t* p, int64_t n_bytes, int64_t piece_len,
+                                  int variant) {
+    if (variant < 0 || variant > 2) throw std::invalid_argument("hash_pieces_variant: unknown variant");
+    if (piece_len <= 0 || piece_len % 16)
+      throw std::invalid_argument("hash_pieces_variant: piece_len must be a positive multiple of 16");
+    if (n_bytes <= 0) throw std::invalid_argument("hash_pieces_variant: empty buffer");
+    const int64_t np = (n_bytes + piece_len - 1) / piece_len;
+    if (np > ((int64_t)1 << 24)) throw std::invalid_argument("hash_pieces_variant: over 2^24 pieces");
+    const int64_t last_len = n_bytes - (np - 1) * piece_len;
+    HIP_CHECK(hipSetDevice(device_));
+    DevMem<uint8_t> data_buf((size_t)n_bytes), out_buf((size_t)np * 20);
+    std::string out((size_t)np * 20, '\0');
+    hipStream_t st = stream_[0];
+    HIP_CHECK(hipMemcpyAsync(data_buf.p, p, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(out_buf.p, 0, out.size(), st));
+    const int block = 64, grid = (int)((np + block - 1) / block);
+    if (variant == 0)
+      hipLaunchKernelGGL((sha1_pieces<16, true, true>), dim3(grid), dim3(block), 0, st,
+                         data_buf.p, piece_len, last_len, (int)np, nullptr, nullptr, out_buf.p);
+    else if (variant == 1)
+      hipLaunchKernelGGL((sha1_pieces<16, false, true>), dim3(grid), dim3(block), 0, st,
+                         data_buf.p, piece_len, last_len, (int)np, nullptr, nullptr, out_buf.p);
+    else
+      hipLaunchKernelGGL((sha1_pieces<16, true, false>), dim3(grid), dim3(block), 0, st,
+                         data_buf.p, piece_len, last_len, (int)np, nullptr, nullptr, out_buf.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(&out[0], out_buf.p, out.size(), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -1717,7 +1770,7 @@ PYBIND11_MODULE(_gpuhash, m) {
       .def(
           "hash_lanes",
           [](GpuVerifier& g, const py::buffer& b, const std::vector<int64_t>& offsets,
-             const std::vector<int64_t>& lengths, const std::string& kernel) {
+             const std::vector<int64_t>& lengths, const std::string& kernel, int64_t base) {
             static const char* names[] = {"split", "split_idle", "lanes16", "lanes1"};
             int k = -1;
             for (int i = 0; i < 4; ++i)
@@ -1729,15 +1782,41 @@ PYBIND11_MODULE(_gpuhash, m) {
             std::string out;
             {
               py::gil_scoped_release rel;
-              out = g.hash_lanes((const uint8_t*)info.ptr, n, offsets, lengths, k);
+              out = g.hash_lanes((const uint8_t*)info.ptr, n, offsets, lengths, k, base);
             }
             return py::bytes(out);
           },
           py::arg("data"), py::arg("offsets"), py::arg("lengths"), py::arg("kernel"),
+          py::arg("base") = (int64_t)0,
           "Test entry: 20 digest bytes per lane from ONE launch of a PartHasher kernel (split = "
           "sha1_lanes_split, split_idle = the same with idle lanes left idle, lanes16, lanes1) "
           "over lanes (offsets[i], lengths[i]) of `data`; ValueError for a lane outside the data "
-          "or, except for lanes1, off 16 bytes")
+          "or, except for lanes1, off 16 bytes. `base` (default 0) places `data` that many bytes "
+          "into the device buffer and adds it to every uploaded offset, as in a PartHasher arena "
+          "of several GiB: a multiple of 256 in 0 .. 8 GiB, anything else is a ValueError; only "
+          "[base, base + len(data) + pad) is written")
+      .def(
+          "hash_pieces_variant",
+          [](GpuVerifier& g, const py::buffer& b, int64_t piece_len, const std::string& variant) {
+            static const char* names[] = {"default", "plain", "noprefetch"};
+            int v = -1;
+            for (int i = 0; i < 3; ++i)
+              if (variant == names[i]) v = i;
+            if (v < 0) throw std::invalid_argument("variant must be default, plain or noprefetch");
+            py::buffer_info info = b.request();
+            const int64_t n = (int64_t)info.size * (int64_t)info.itemsize;
+            std::string out;
+            {
+              py::gil_scoped_release rel;
+              out = g.hash_pieces_variant((const uint8_t*)info.ptr, n, piece_len, v);
+            }
+            return py::bytes(out);
+          },
+          py::arg("data"), py::arg("piece_len"), py::arg("variant"),
+          "Test entry: digests from ONE launch of sha1_pieces<16, B3, PF> on `data` - default = "
+          "<true, true>, plain = <false, true> (plain C rounds), noprefetch = <true, false>, the "
+          "arms of kernel_bench / kernel_bench_prefetch; ValueError for a piece_len that is no "
+          "multiple of 16, an unknown variant or an empty buffer")
       .def_property_readonly("batch_bytes", &GpuVerifier::batch_bytes);
   py::class_<PartHasher>(m, "PartHasher")
       .def(py::init([](int device, int64_t slot_bytes, int slots, int streams, int max_lanes,
