@@ -1623,6 +1623,20 @@ py::dict part_stats(PartHasher& h) {
   return d;
 }
 
+// The buffer entry points below hash size * itemsize bytes from info.ptr, which are the
+// view's bytes only when it is one C-ordered run: a stepped, reversed or column slice is
+// refused (ValueError) before any HIP call. Extents of 1 may carry any stride; an empty view
+// is contiguous.
+void require_c_contiguous(const py::buffer_info& info) {
+  if (info.size == 0) return;
+  py::ssize_t want = info.itemsize;
+  for (py::ssize_t d = info.ndim; d-- > 0;) {
+    if (info.shape[(size_t)d] != 1 && info.strides[(size_t)d] != want)
+      throw std::invalid_argument("buffer must be C-contiguous");
+    want *= info.shape[(size_t)d];
+  }
+}
+
 int device_count() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) {
@@ -1662,6 +1676,7 @@ PYBIND11_MODULE(_gpuhash, m) {
           "hash_buffer",
           [](GpuVerifier& g, const py::buffer& b, int64_t piece_len) {
             py::buffer_info info = b.request();
+            require_c_contiguous(info);
             int64_t n = (int64_t)info.size * (int64_t)info.itemsize;
             if (piece_len <= 0) throw std::invalid_argument("piece_len must be > 0");
             std::string out;
@@ -1778,6 +1793,7 @@ PYBIND11_MODULE(_gpuhash, m) {
             if (k < 0)
               throw std::invalid_argument("kernel must be split, split_idle, lanes16 or lanes1");
             py::buffer_info info = b.request();
+            require_c_contiguous(info);
             const int64_t n = (int64_t)info.size * (int64_t)info.itemsize;
             std::string out;
             {
@@ -1804,6 +1820,7 @@ PYBIND11_MODULE(_gpuhash, m) {
               if (variant == names[i]) v = i;
             if (v < 0) throw std::invalid_argument("variant must be default, plain or noprefetch");
             py::buffer_info info = b.request();
+            require_c_contiguous(info);
             const int64_t n = (int64_t)info.size * (int64_t)info.itemsize;
             std::string out;
             {
@@ -1839,6 +1856,7 @@ PYBIND11_MODULE(_gpuhash, m) {
           [](PartHasher& h, const py::buffer& b, int64_t piece_len) {
             // test / bench entry: the buffer is registered, submitted and waited for here
             py::buffer_info info = b.request();
+            require_c_contiguous(info);
             const int64_t n = (int64_t)info.size * (int64_t)info.itemsize;
             const int64_t np = piece_len > 0 ? (n + piece_len - 1) / piece_len : 0;
             std::string out((size_t)np * 20, '\0');

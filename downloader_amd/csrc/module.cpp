@@ -23,10 +23,23 @@ struct BufView {
   py::buffer_info info;  // keeps the exporter alive/locked
 };
 
+// The callers hash size * itemsize bytes from info.ptr, which are the view's bytes only when
+// it is one C-ordered run: a stepped, reversed or column slice is refused (ValueError), in any
+// dimension and whatever its item size. Extents of 1 may carry any stride; an empty view is
+// contiguous.
+bool c_contiguous(const py::buffer_info& info) {
+  if (info.size == 0) return true;
+  py::ssize_t want = info.itemsize;
+  for (py::ssize_t d = info.ndim; d-- > 0;) {
+    if (info.shape[(size_t)d] != 1 && info.strides[(size_t)d] != want) return false;
+    want *= info.shape[(size_t)d];
+  }
+  return true;
+}
+
 BufView view(const py::buffer& b) {
   py::buffer_info info = b.request();
-  if (info.ndim > 1 && info.strides.back() != info.itemsize)
-    throw std::invalid_argument("buffer must be C-contiguous");
+  if (!c_contiguous(info)) throw std::invalid_argument("buffer must be C-contiguous");
   size_t n = (size_t)info.size * (size_t)info.itemsize;
   return BufView{(const uint8_t*)info.ptr, n, std::move(info)};
 }
