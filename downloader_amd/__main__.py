@@ -5,7 +5,8 @@
   python -m downloader_amd broker      [--port 5672]  bundled AMQP 0-9-1 broker
   python -m downloader_amd submit      ID SOURCE URI [--type TV]   publish an api.Download
   python -m downloader_amd make-torrent PATH -o F [--webseed URL] [--tracker URL]
-  python -m downloader_amd verify      TORRENT DIR [--backend gpu|cpu|auto]
+                                       [--meta-version 1|2]
+  python -m downloader_amd verify      TORRENT DIR [--backend gpu|cpu|auto] [--merkle]
   python -m downloader_amd config                     print the effective config
   python -m downloader_amd doctor      [--sharers N]  host readiness report (JSON + warnings)
 
@@ -95,6 +96,17 @@ def _submit(args) -> int:
 
 def _make_torrent(args) -> int:
     from .torrent.metainfo import make_torrent, parse_torrent
+    if args.meta_version == 2:
+        from .torrent.metainfo_v2 import make_torrent_v2, parse_torrent_v2
+        raw = make_torrent_v2(args.path, args.piece_length, args.tracker or [],
+                              args.webseed or [])
+        with open(args.output, "wb") as f:
+            f.write(raw)
+        m2 = parse_torrent_v2(raw)
+        print(json.dumps({"info_hash": m2.info_hash_v2.hex(), "pieces": m2.num_pieces,
+                          "piece_length": m2.piece_length, "bytes": m2.total_length,
+                          "meta_version": 2}))
+        return 0
     raw = make_torrent(args.path, args.piece_length, args.tracker or [], args.webseed or [])
     with open(args.output, "wb") as f:
         f.write(raw)
@@ -104,11 +116,40 @@ def _make_torrent(args) -> int:
     return 0
 
 
+def _verify_v2(args, m2) -> int:
+    """Recheck through the merkle trees (BEP 52): file by file against its piece layer, or its
+    pieces root when it is no larger than a piece."""
+    from .torrent import merkle
+    backend = merkle.choose_backend(args.backend, m2.total_length, recheck=True)
+    t0 = time.perf_counter()
+    ok = b"".join(merkle.verify_file(p, f.length, m2.piece_length, m2.expected(f), backend=backend)
+                  for (p, _), f in zip(m2.local_files(args.dir), m2.files) if f.length)
+    dt = time.perf_counter() - t0
+    good = sum(ok)
+    print(json.dumps({"pieces": len(ok), "good": good, "seconds": round(dt, 4),
+                      "GBps": round(m2.total_length / dt / 1e9, 3) if dt else None,
+                      "backend": backend, "meta_version": 2}))
+    return 0 if good == len(ok) else 1
+
+
 def _verify(args) -> int:
     from .ops import hashing
-    from .torrent.metainfo import parse_torrent
+    from .torrent.metainfo import MetainfoError, parse_torrent
+    from .torrent.metainfo_v2 import parse_torrent_v2
     with open(args.torrent, "rb") as f:
-        m = parse_torrent(f.read())
+        data = f.read()
+    if args.merkle:                      # a hybrid torrent, rechecked as the v2 torrent it is
+        return _verify_v2(args, parse_torrent_v2(data))
+    try:
+        m = parse_torrent(data)
+    except MetainfoError:
+        try:
+            m2 = parse_torrent_v2(data)
+        except MetainfoError:
+            m2 = None
+        if m2 is None:
+            raise                        # not a v2 torrent either: the v1 parser's error stands
+        return _verify_v2(args, m2)
     files = m.local_files(args.dir)
     t0 = time.perf_counter()
     ok = hashing.verify_pieces(files, m.piece_length, m.pieces, backend=args.backend)
@@ -187,10 +228,14 @@ def main(argv=None) -> int:
     mt.add_argument("--piece-length", type=int, default=0)
     mt.add_argument("--tracker", action="append")
     mt.add_argument("--webseed", action="append")
+    mt.add_argument("--meta-version", type=int, choices=[1, 2], default=1,
+                    help="2: a v2-only torrent (BEP 52 merkle trees)")
     v = sub.add_parser("verify")
     v.add_argument("torrent")
     v.add_argument("dir")
     v.add_argument("--backend", default="auto", choices=["auto", "cpu", "gpu"])
+    v.add_argument("--merkle", action="store_true",
+                   help="recheck a hybrid torrent through its v2 merkle trees")
     c = sub.add_parser("config")
     c.add_argument("--config", default="")
     c.add_argument("--show-secrets", action="store_true", help="do not mask credentials")

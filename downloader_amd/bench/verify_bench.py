@@ -9,7 +9,14 @@ Reports (JSON lines):
   * ``verify``  - end-to-end recheck of a multi-file torrent that sits in the page cache:
     CPU (threaded native SHA-1) vs GPU (pread -> pinned -> H2D -> kernel, double-buffered).
 
+  * ``merkle``  - (``--mode merkle``) BitTorrent v2: a v2 torrent of the files is created and
+    rechecked through the SHA-256 merkle trees by both backends in one process, alternating;
+    ONE JSON line with ``cpu_GBps``, ``gpu_GBps`` (best of ``--repeat`` rounds each, every
+    round listed), the kernel-only rate of ``sha256_leaves`` on 1 GiB of device-resident
+    leaves and the summed time of the ``sha256_pairs`` launches that reduce them to one root.
+
   python -m downloader_amd.bench.verify_bench --gib 4 --piece-mb 1
+  python -m downloader_amd.bench.verify_bench --mode merkle --gib 4 --piece-mb 1
 """
 from __future__ import annotations
 
@@ -65,8 +72,58 @@ def make_files(root: str, total: int, nfiles: int):
     return files
 
 
+def merkle_mode(a) -> int:
+    from downloader_amd.ops import gpu_available, gpumerkle
+    from downloader_amd.torrent import merkle
+    from downloader_amd.torrent.metainfo_v2 import make_torrent_v2, parse_torrent_v2
+    if not gpu_available():
+        print("no HIP device", file=sys.stderr)
+        return 2
+    plen = int(a.piece_mb * (1 << 20))
+    files = make_files(os.path.join(a.dir, "v2"), int(a.gib * (1 << 30)), a.files)
+    total = sum(n for _, n in files)
+    try:
+        m = parse_torrent_v2(make_torrent_v2(os.path.join(a.dir, "v2"), plen, threads=a.threads))
+        local = m.local_files(a.dir)
+        assert sorted(local) == sorted(files)
+
+        def recheck(backend: str) -> float:
+            t0 = time.perf_counter()
+            ok = b"".join(merkle.verify_file(p, f.length, plen, m.expected(f), backend=backend,
+                                             threads=a.threads)
+                          for (p, _), f in zip(local, m.files))
+            dt = time.perf_counter() - t0
+            assert ok == b"\x01" * m.num_pieces, f"{backend} recheck found bad pieces"
+            return total / dt / 1e9
+
+        h = merkle.gpu_hasher()
+        recheck("gpu")                     # warm-up: code objects, first touch of the slots
+        cpu, gpu = [], []
+        for _ in range(a.repeat):
+            cpu.append(recheck("cpu"))
+            gpu.append(recheck("gpu"))
+        n_leaves = 1 << 16                 # 1 GiB of device-resident leaves
+        with merkle._call_lock:
+            ms_leaves, ms_pairs = h.kernel_bench(n_leaves, 3)
+        emit({"section": "merkle", "arch": gpumerkle().arch(), "bytes": total,
+              "files": len(files), "piece_len": plen, "pieces": m.num_pieces,
+              "cpu_threads": a.threads, "gpu_readers": 8, "gpu_batch_bytes": h.batch_bytes,
+              "cpu_GBps": round(max(cpu), 2), "gpu_GBps": round(max(gpu), 2),
+              "cpu_GBps_rounds": [round(x, 2) for x in cpu],
+              "gpu_GBps_rounds": [round(x, 2) for x in gpu],
+              "gpu_vs_cpu": round(max(gpu) / max(cpu), 3),
+              "leaves_kernel_GBps": round(n_leaves * 16384 / 1e9 / (ms_leaves / 1e3), 1),
+              "leaves_kernel_ms": round(ms_leaves, 3), "kernel_leaves": n_leaves,
+              "pairs_ms": round(ms_pairs, 3), "pairs_launches": 16})
+    finally:
+        shutil.rmtree(a.dir, ignore_errors=True)
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["sha1", "merkle"], default="sha1",
+                    help="sha1: the v1 sections; merkle: the BitTorrent v2 recheck line")
     ap.add_argument("--gib", type=float, default=4.0)
     ap.add_argument("--piece-mb", type=float, default=1.0)
     ap.add_argument("--files", type=int, default=8)
@@ -82,6 +139,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+    if a.mode == "merkle":
+        return merkle_mode(a)
     from downloader_amd.ops import gpu_available, gpuhash, hashing
     if not gpu_available():
         print("no HIP device", file=sys.stderr)

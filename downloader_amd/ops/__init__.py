@@ -3,10 +3,12 @@
 * ``_native``  (host C++, pybind11): OpenSSL-EVP hashing on a GIL-free thread pool and the
   zero-copy HTTP transport (splice / sendfile).
 * ``_gpuhash`` (HIP, gfx950): batched SHA-1 piece verification on the MI355X.
+* ``_gpumerkle`` (HIP, gfx950): BEP 52 (BitTorrent v2) SHA-256 merkle hashing, one lane per
+  16 KiB block.
 
-Both are built in-tree by ``downloader_amd.ops.build`` (``__graft_entry__.build()``). A
-missing extension is an error, not a silent fallback: ``native()`` / ``gpuhash()`` raise
-with the build command in the message.
+All are built in-tree by ``downloader_amd.ops.build`` (``__graft_entry__.build()``). A
+missing extension is an error, not a silent fallback: ``native()`` / ``gpuhash()`` /
+``gpumerkle()`` raise with the build command in the message.
 """
 from __future__ import annotations
 
@@ -17,6 +19,7 @@ from typing import Optional
 
 _native: Optional[ModuleType] = None
 _gpu: Optional[ModuleType] = None
+_merkle: Optional[ModuleType] = None
 
 
 class NativeBuildMissing(ImportError):
@@ -51,6 +54,13 @@ def gpuhash() -> ModuleType:
     if _gpu is None:
         _gpu = _load("_gpuhash")
     return _gpu
+
+
+def gpumerkle() -> ModuleType:
+    global _merkle
+    if _merkle is None:
+        _merkle = _load("_gpumerkle")
+    return _merkle
 
 
 def gpu_available() -> bool:

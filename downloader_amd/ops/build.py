@@ -3,6 +3,7 @@
 Targets
   * ``_native``   host C++17 pybind11 module: OpenSSL EVP hashing + zero-copy HTTP transport
   * ``_gpuhash``  HIP/gfx950 pybind11 module: batched SHA-1 piece verification on the MI355X
+  * ``_gpumerkle`` HIP/gfx950 pybind11 module: BEP 52 (BitTorrent v2) SHA-256 merkle hashing
   * ``blobd``     C++ multi-threaded HTTP origin + S3 sink used by the bench harness
 
 Run ``python -m downloader_amd.ops.build`` (``__graft_entry__.build()`` calls it).
@@ -86,6 +87,18 @@ def build_gpuhash(force: bool = False, verbose: bool = True) -> Path:
     return out
 
 
+def build_gpumerkle(force: bool = False, verbose: bool = True) -> Path:
+    """BEP 52 SHA-256 merkle kernels (csrc/gpu_sha256_merkle.hip): a module of its own."""
+    srcs = [CSRC / "gpu_sha256_merkle.hip"]
+    out = OPS / f"_gpumerkle{EXT}"
+    if force or _stale(out, srcs):
+        hipcc = str(ROCM / "bin" / "hipcc")
+        cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
+               "-fvisibility=hidden", *_pybind_includes(), str(srcs[0]), "-o", str(out)]
+        _run(cmd, verbose)
+    return out
+
+
 def build_blobd(force: bool = False, verbose: bool = True) -> Path:
     srcs = [CSRC / "blobd.cpp"]
     BIN.mkdir(exist_ok=True)
@@ -156,6 +169,8 @@ def build_all(force: bool = False, verbose: bool = True, gpu: bool = True) -> No
         if not (ROCM / "bin" / "hipcc").exists():
             raise RuntimeError("hipcc not found; cannot build the gfx950 kernels")
         build_gpuhash(force, verbose)
+        if (CSRC / "gpu_sha256_merkle.hip").exists():
+            build_gpumerkle(force, verbose)
 
 
 def clean() -> None:

@@ -67,6 +67,10 @@ def new(algo: str):
 def hash_pieces(data, piece_len: int, algo: str = "sha1", threads: int = 0,
                 backend: str = "cpu") -> bytes:
     if backend == "gpu":
+        if algo == "sha256" and piece_len == 16384:
+            # the BEP 52 leaf layer: the one SHA-256 shape the device has (ops._gpumerkle)
+            from ..torrent import merkle
+            return merkle.leaf_hashes(data, backend="gpu")
         if algo != "sha1":
             raise ValueError("GPU backend implements SHA-1 only")
         return _verifier().hash_buffer(data, piece_len)
