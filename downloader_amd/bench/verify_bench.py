@@ -10,13 +10,18 @@ Reports (JSON lines):
     CPU (threaded native SHA-1) vs GPU (pread -> pinned -> H2D -> kernel, double-buffered).
 
   * ``merkle``  - (``--mode merkle``) BitTorrent v2: a v2 torrent of the files is created and
-    rechecked through the SHA-256 merkle trees by both backends in one process, alternating;
-    ONE JSON line with ``cpu_GBps``, ``gpu_GBps`` (best of ``--repeat`` rounds each, every
-    round listed), the kernel-only rate of ``sha256_leaves`` on 1 GiB of device-resident
+    rechecked through the SHA-256 merkle trees in one process by three arms, alternating: the
+    host, the device file by file (``MerkleHasher.verify_file`` per file) and the device with
+    pieces of many files per batch (``MerkleHasher.verify_files``, one call). ONE JSON line
+    with ``cpu_GBps``, ``gpu_GBps``, ``gpu_batched_GBps`` (best of ``--repeat`` rounds each,
+    every round listed), the kernel-only rate of ``sha256_leaves`` on 1 GiB of device-resident
     leaves and the summed time of the ``sha256_pairs`` launches that reduce them to one root.
+    ``--small-files N`` adds N files of 1 byte to 4 pieces (log-uniform, fixed seed) to the
+    large ones: the shape of a release with subtitles, artwork and samples.
 
   python -m downloader_amd.bench.verify_bench --gib 4 --piece-mb 1
   python -m downloader_amd.bench.verify_bench --mode merkle --gib 4 --piece-mb 1
+  python -m downloader_amd.bench.verify_bench --mode merkle --gib 4 --piece-mb 1 --small-files 4096
 """
 from __future__ import annotations
 
@@ -72,6 +77,22 @@ def make_files(root: str, total: int, nfiles: int):
     return files
 
 
+def make_small_files(root: str, n: int, max_len: int):
+    """n files of 1 .. max_len bytes, sizes log-uniform, from a fixed seed."""
+    import math
+    import random
+    rng = random.Random(4321)
+    os.makedirs(root, exist_ok=True)
+    files = []
+    for i in range(n):
+        size = min(max_len, max(1, int(math.exp(rng.uniform(0.0, math.log(max_len))))))
+        p = os.path.join(root, f"s{i:05d}.srt")
+        with open(p, "wb") as f:
+            f.write(rng.randbytes(size))
+        files.append((p, size))
+    return files
+
+
 def merkle_mode(a) -> int:
     from downloader_amd.ops import gpu_available, gpumerkle
     from downloader_amd.torrent import merkle
@@ -81,6 +102,8 @@ def merkle_mode(a) -> int:
         return 2
     plen = int(a.piece_mb * (1 << 20))
     files = make_files(os.path.join(a.dir, "v2"), int(a.gib * (1 << 30)), a.files)
+    if a.small_files:
+        files += make_small_files(os.path.join(a.dir, "v2", "extras"), a.small_files, 4 * plen)
     total = sum(n for _, n in files)
     try:
         m = parse_torrent_v2(make_torrent_v2(os.path.join(a.dir, "v2"), plen, threads=a.threads))
@@ -97,21 +120,38 @@ def merkle_mode(a) -> int:
             return total / dt / 1e9
 
         h = merkle.gpu_hasher()
+        expected = b"".join(m.expected(f) for f in m.files)
+
+        def recheck_batched() -> float:
+            t0 = time.perf_counter()
+            with merkle._call_lock:
+                ok = h.verify_files(local, plen, expected)
+            dt = time.perf_counter() - t0
+            assert ok == b"\x01" * m.num_pieces, "batched recheck found bad pieces"
+            return total / dt / 1e9
+
         recheck("gpu")                     # warm-up: code objects, first touch of the slots
-        cpu, gpu = [], []
+        recheck_batched()
+        cpu, gpu, batched = [], [], []
         for _ in range(a.repeat):
             cpu.append(recheck("cpu"))
             gpu.append(recheck("gpu"))
+            batched.append(recheck_batched())
         n_leaves = 1 << 16                 # 1 GiB of device-resident leaves
         with merkle._call_lock:
             ms_leaves, ms_pairs = h.kernel_bench(n_leaves, 3)
         emit({"section": "merkle", "arch": gpumerkle().arch(), "bytes": total,
-              "files": len(files), "piece_len": plen, "pieces": m.num_pieces,
+              "files": len(files), "small_files": a.small_files, "piece_len": plen,
+              "pieces": m.num_pieces,
               "cpu_threads": a.threads, "gpu_readers": 8, "gpu_batch_bytes": h.batch_bytes,
               "cpu_GBps": round(max(cpu), 2), "gpu_GBps": round(max(gpu), 2),
+              "gpu_batched_GBps": round(max(batched), 2),
               "cpu_GBps_rounds": [round(x, 2) for x in cpu],
               "gpu_GBps_rounds": [round(x, 2) for x in gpu],
+              "gpu_batched_GBps_rounds": [round(x, 2) for x in batched],
               "gpu_vs_cpu": round(max(gpu) / max(cpu), 3),
+              "batched_vs_gpu": round(max(batched) / max(gpu), 3),
+              "batched_vs_cpu": round(max(batched) / max(cpu), 3),
               "leaves_kernel_GBps": round(n_leaves * 16384 / 1e9 / (ms_leaves / 1e3), 1),
               "leaves_kernel_ms": round(ms_leaves, 3), "kernel_leaves": n_leaves,
               "pairs_ms": round(ms_pairs, 3), "pairs_launches": 16})
@@ -134,6 +174,8 @@ def main(argv=None) -> int:
     ap.add_argument("--chunk-kb", type=int, default=64, help="streamed path chunk per lane")
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--small-files", type=int, default=0,
+                    help="merkle mode: this many files of 1 byte .. 4 pieces besides the large ones")
     ap.add_argument("--kernel-sizes", default="256,1024,4096", help="kernel section piece KiB")
     ap.add_argument("--kernel-counts", default="1024,4096,16384", help="kernel section pieces")
     a = ap.parse_args(argv)

@@ -24,6 +24,11 @@
 //     the leaves-per-piece count before reduction (a missing leaf is 32 zero bytes), so every
 //     level halves uniformly. The piece layer is reduced to the root on the device too, padded
 //     to a power of two with the pad hash of its level.
+//   * hash_files / verify_files take a whole torrent's files: a batch holds units (pieces, or
+//     whole small files) of many files at once, laid out by merkle_plan.h so that ONE
+//     sha256_leaf_table launch (one lane per leaf-table entry) and ONE sha256_pairs_fin launch
+//     per level reduce subtrees of different heights together; the batch loop drains a slot
+//     only when it comes round again, so fills and device work overlap across files.
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -42,7 +47,10 @@
 #include <unistd.h>
 #include <vector>
 
+#include "merkle_plan.h"
+
 namespace py = pybind11;
+namespace mp = stager::merkle_plan;
 
 // A failed call stays behind as the thread's "last error" until hipGetLastError() reads it, and
 // every launch here is checked with hipGetLastError(): the error is taken off the thread as it
@@ -60,6 +68,10 @@ namespace py = pybind11;
 namespace {
 
 constexpr int64_t kLeaf = 16384;  // BEP 52 block size
+static_assert(kLeaf == mp::kLeaf, "the plan and the kernels share the block size");
+
+using PlanLeaf = mp::Leaf;  // one lane of sha256_leaf_table reads its entry as one 16-byte load
+static_assert(sizeof(PlanLeaf) == 16 && alignof(PlanLeaf) == 8, "leaf table entry layout");
 
 __device__ __forceinline__ uint32_t rotr(uint32_t x, int n) {
   return __builtin_amdgcn_alignbit(x, x, n);
@@ -205,17 +217,12 @@ __device__ __forceinline__ void store_digest(uint8_t* o, const Sha256State& s) {
   q[1] = make_uint4(bswap(s.h[4]), bswap(s.h[5]), bswap(s.h[6]), bswap(s.h[7]));
 }
 
-// Lane i: SHA-256 of the 16 KiB block at data + i * 16384 (the last lane: last_len bytes,
-// 1 .. 16384), digest to out + 32 * i. Whole blocks, then tail + padding built word by word
-// into w[]: a remainder of 56 bytes or more takes two padding blocks, a remainder of 0 (every
-// full leaf) one whole padding block. Tail bytes are read one by one and only below `rem`.
-__global__ __launch_bounds__(64) void sha256_leaves(const uint8_t* __restrict__ data,
-                                                    int64_t n_leaves, int last_len,
-                                                    uint8_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_leaves) return;
-  const int len = (i == n_leaves - 1) ? last_len : (int)kLeaf;
-  const uint8_t* p = data + i * kLeaf;
+// One leaf: SHA-256 of the `len` bytes (1 .. 16384) at p (16-byte aligned), digest to o. Whole
+// blocks, then tail + padding built word by word into w[]: a remainder of 56 bytes or more
+// takes two padding blocks, a remainder of 0 (every full leaf) one whole padding block. Tail
+// bytes are read one by one and only below `rem`: nothing at or past p + len is touched.
+__device__ __forceinline__ void sha256_leaf(const uint8_t* __restrict__ p, int len,
+                                            uint8_t* __restrict__ o) {
   Sha256State s;
   sha256_init(s);
   const int nfull = len >> 6;
@@ -243,7 +250,46 @@ __global__ __launch_bounds__(64) void sha256_leaves(const uint8_t* __restrict__ 
     }
     sha256_block(s, w);
   }
-  store_digest(out + i * 32, s);
+  store_digest(o, s);
+}
+
+// Lane i: the 16 KiB block at data + i * 16384 (the last lane: last_len bytes, 1 .. 16384),
+// digest to out + 32 * i.
+__global__ __launch_bounds__(64) void sha256_leaves(const uint8_t* __restrict__ data,
+                                                    int64_t n_leaves, int last_len,
+                                                    uint8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_leaves) return;
+  const int len = (i == n_leaves - 1) ? last_len : (int)kLeaf;
+  sha256_leaf(data + i * kLeaf, len, out + i * 32);
+}
+
+// Lane i: leaf i of a batch plan's leaf table (merkle_plan.h): table[i].len bytes at
+// data + table[i].src, digest to out + 32 * table[i].dst. The slot holds pieces of many files;
+// the bytes between two files are stale data of an earlier batch and no lane reads them.
+__global__ __launch_bounds__(64) void sha256_leaf_table(const uint8_t* __restrict__ data,
+                                                        const PlanLeaf* __restrict__ table,
+                                                        int64_t n_leaves,
+                                                        uint8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_leaves) return;
+  const PlanLeaf e = table[i];
+  sha256_leaf(data + e.src, e.len, out + (int64_t)e.dst * 32);
+}
+
+// SHA-256 of the 64 bytes at p (two child digests).
+__device__ __forceinline__ void sha256_pair(Sha256State& s, const uint8_t* __restrict__ p) {
+  sha256_init(s);
+  uint4 v[4];
+  uint32_t w[16];
+  load_raw16(p, v);
+  to_words(v, w);
+  sha256_block(s, w);
+  w[0] = 0x80000000u;  // the padding block of a 512-bit message
+#pragma unroll
+  for (int k = 1; k < 15; ++k) w[k] = 0;
+  w[15] = 512u;
+  sha256_block(s, w);
 }
 
 // Lane i: SHA-256 of the 64 bytes at in + 64 * i (two child digests) -> out + 32 * i.
@@ -252,18 +298,23 @@ __global__ __launch_bounds__(64) void sha256_pairs(const uint8_t* __restrict__ i
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   Sha256State s;
-  sha256_init(s);
-  uint4 v[4];
-  uint32_t w[16];
-  load_raw16(in + i * 64, v);
-  to_words(v, w);
-  sha256_block(s, w);
-  w[0] = 0x80000000u;  // the padding block of a 512-bit message
-#pragma unroll
-  for (int k = 1; k < 15; ++k) w[k] = 0;
-  w[15] = 512u;
-  sha256_block(s, w);
+  sha256_pair(s, in + i * 64);
   store_digest(out + i * 32, s);
+}
+
+// One level of a batch plan: sha256_pairs over the units still being reduced, and the outputs
+// from fin_start on are finished unit nodes, written to result + 32 * (unit_base + i -
+// fin_start) as well (the sorted unit order of merkle_plan.h).
+__global__ __launch_bounds__(64) void sha256_pairs_fin(const uint8_t* __restrict__ in, int64_t n,
+                                                       uint8_t* __restrict__ out,
+                                                       int64_t fin_start, int64_t unit_base,
+                                                       uint8_t* __restrict__ result) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Sha256State s;
+  sha256_pair(s, in + i * 64);
+  store_digest(out + i * 32, s);
+  if (i >= fin_start) store_digest(result + (unit_base + i - fin_start) * 32, s);
 }
 
 void launch_leaves(hipStream_t st, const uint8_t* d_data, int64_t n, int last_len, uint8_t* d_out) {
@@ -277,6 +328,22 @@ void launch_pairs(hipStream_t st, const uint8_t* d_in, int64_t n, uint8_t* d_out
   if (n <= 0) return;
   hipLaunchKernelGGL(sha256_pairs, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, d_in, n,
                      d_out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_leaf_table(hipStream_t st, const uint8_t* d_data, const PlanLeaf* d_table, int64_t n,
+                       uint8_t* d_out) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(sha256_leaf_table, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, d_data,
+                     d_table, n, d_out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_pairs_fin(hipStream_t st, const uint8_t* d_in, const mp::Level& lv, uint8_t* d_out,
+                      uint8_t* d_result) {
+  if (lv.n_pairs <= 0) return;
+  hipLaunchKernelGGL(sha256_pairs_fin, dim3((unsigned)((lv.n_pairs + 63) / 64)), dim3(64), 0, st,
+                     d_in, lv.n_pairs, d_out, lv.fin_start, lv.unit_base, d_result);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -361,6 +428,7 @@ int log2_exact(int64_t v) {
 }
 
 using Digest = std::array<uint8_t, 32>;
+using FileList = std::vector<std::pair<std::string, int64_t>>;  // (path, length)
 
 struct Tree {
   std::string layer;  // 32 bytes per piece; empty when the file is no larger than a piece
@@ -506,6 +574,35 @@ class MerkleHasher {
     return ok;
   }
 
+  // 32 bytes per unit (merkle_plan.h: a piece of a file longer than piece_len, or a whole
+  // smaller file), file order then piece order: the piece layers and the roots of the small
+  // files, concatenated. A missing or short file is an error.
+  std::string hash_files(const FileList& files, int64_t piece_len) {
+    std::string out((size_t)total_units(files, piece_len) * 32, '\0');
+    run_files(files, piece_len, (uint8_t*)out.data(), nullptr);
+    return out;
+  }
+
+  // One byte per unit against `expected` (32 bytes per unit, the order of hash_files). A unit
+  // its file on disk does not cover is 0; the other files of its batch are not affected.
+  std::vector<uint8_t> verify_files(const FileList& files, int64_t piece_len,
+                                    const std::string& expected) {
+    const int64_t nu = total_units(files, piece_len);
+    std::string got((size_t)nu * 32, '\0');
+    std::vector<uint8_t> ok((size_t)nu, 1);
+    run_files(files, piece_len, (uint8_t*)got.data(), ok.data());
+    for (int64_t i = 0; i < nu; ++i)
+      ok[(size_t)i] = ok[(size_t)i] &&
+                      memcmp(got.data() + i * 32, expected.data() + i * 32, 32) == 0;
+    return ok;
+  }
+
+  static int64_t total_units(const FileList& files, int64_t piece_len) {
+    int64_t n = 0;
+    for (const auto& f : files) n += mp::unit_count(f.second, piece_len);
+    return n;
+  }
+
   // Kernel-only timing on device-resident data (hipEvents): ms per sha256_leaves launch over
   // n_leaves full leaves, and the summed ms of the log2(n_leaves) sha256_pairs launches that
   // reduce them to one root. n_leaves: a power of two.
@@ -548,9 +645,138 @@ class MerkleHasher {
       if (h_dig_[s]) hipHostFree(h_dig_[s]);
       for (int b = 0; b < 2; ++b)
         if (d_dig_[s][b]) hipFree(d_dig_[s][b]);
+      if (h_tab_[s]) hipHostFree(h_tab_[s]);
+      if (d_tab_[s]) hipFree(d_tab_[s]);
+      if (d_res_[s]) hipFree(d_res_[s]);
       if (stream_[s]) hipStreamDestroy(stream_[s]);
       stream_[s] = nullptr;
-      h_buf_[s] = d_buf_[s] = h_dig_[s] = d_dig_[s][0] = d_dig_[s][1] = nullptr;
+      h_buf_[s] = d_buf_[s] = h_dig_[s] = d_dig_[s][0] = d_dig_[s][1] = d_res_[s] = nullptr;
+      h_tab_[s] = d_tab_[s] = nullptr;
+    }
+  }
+
+  // Leaf tables (pinned host + device) and the per-unit result buffers of the multi-file
+  // entries: one per slot, sized for batch_bytes / 16384 leaves and units, allocated by the
+  // first hash_files / verify_files call.
+  void ensure_plan_buffers() {
+    const size_t cap = (size_t)(batch_bytes_ / kLeaf);
+    for (int s = 0; s < 2; ++s) {
+      if (!h_tab_[s])
+        HIP_CHECK(hipHostMalloc((void**)&h_tab_[s], cap * sizeof(PlanLeaf), hipHostMallocDefault));
+      if (!d_tab_[s]) HIP_CHECK(hipMalloc((void**)&d_tab_[s], cap * sizeof(PlanLeaf)));
+      if (!d_res_[s]) HIP_CHECK(hipMalloc((void**)&d_res_[s], dig_bytes_));
+    }
+  }
+
+  // Reads of batch `b` into slot s: the reader threads work through the read list in ranges
+  // of at most kFillChunk, each opening the file for its range and closing it again (a batch
+  // may name tens of thousands of files). What pread did not deliver is zeroed. A unit its file
+  // does not cover is marked 0 in `readable` (one byte per unit of the batch); without
+  // `readable` it is an error.
+  void fill_batch(const FileList& files, const mp::Batch& b, int s, uint8_t* readable) {
+    struct Chunk {
+      size_t read;
+      int64_t off, len;
+    };
+    std::vector<Chunk> chunks;
+    for (size_t r = 0; r < b.reads.size(); ++r)
+      for (int64_t o = 0; o < b.reads[r].len; o += kFillChunk)
+        chunks.push_back(Chunk{r, o, std::min(kFillChunk, b.reads[r].len - o)});
+    std::vector<std::atomic<int64_t>> good(b.reads.size());  // delivered prefix per read
+    for (size_t r = 0; r < b.reads.size(); ++r) good[r].store(b.reads[r].len);
+    parallel_for(chunks.size(), readers_, [&](size_t c) {
+      const Chunk& ch = chunks[c];
+      const mp::Read& rd = b.reads[ch.read];
+      uint8_t* dst = h_buf_[s] + rd.slot_off + ch.off;
+      int64_t got = 0;
+      {
+        Fd f(files[(size_t)rd.file].first);
+        while (f.fd >= 0 && got < ch.len) {
+          ssize_t n = pread(f.fd, dst + got, (size_t)(ch.len - got), rd.file_off + ch.off + got);
+          if (n < 0 && errno == EINTR) continue;
+          if (n <= 0) break;
+          got += n;
+        }
+      }
+      if (got < ch.len) {
+        memset(dst + got, 0, (size_t)(ch.len - got));
+        int64_t at = ch.off + got, cur = good[ch.read].load();
+        while (at < cur && !good[ch.read].compare_exchange_weak(cur, at)) {
+        }
+      }
+    });
+    size_t u = 0;  // units and reads are both in file order, one read per file of the batch
+    for (size_t r = 0; r < b.reads.size(); ++r) {
+      const mp::Read& rd = b.reads[r];
+      const int64_t g = good[r].load();
+      for (; u < b.units.size() && b.units[u].file == rd.file; ++u) {
+        if (b.units[u].slot_off + b.units[u].bytes - rd.slot_off <= g) continue;
+        if (!readable)
+          throw std::runtime_error("cannot read " + files[(size_t)rd.file].first + ": short at byte " +
+                                   std::to_string(rd.file_off + g));
+        readable[u] = 0;
+      }
+    }
+  }
+
+  // The batch loop of the multi-file entries: 32 bytes per unit into `nodes`. Batch i + 1 is
+  // planned and read into its slot while batch i copies and hashes on the other slot's stream;
+  // a slot is drained only when it comes round again, so fills and device work overlap across
+  // file boundaries. Per batch: two H2D copies (data, leaf table), one memset of the level-0
+  // digests when leaves are missing, ONE sha256_leaf_table launch, one D2D copy of the width-1
+  // units' leaf digests, ONE sha256_pairs_fin launch per level and one D2H copy of the nodes.
+  void run_files(const FileList& files, int64_t piece_len, uint8_t* nodes, uint8_t* readable) {
+    HIP_CHECK(hipSetDevice(device_));
+    ensure_plan_buffers();
+    std::vector<int64_t> lengths;
+    lengths.reserve(files.size());
+    for (const auto& f : files) lengths.push_back(f.second);
+    mp::Planner planner(std::move(lengths), piece_len, batch_bytes_);
+    mp::Batch plan[2];
+    bool live[2] = {false, false};
+    auto drain = [&](int s) {
+      if (!live[s]) return;
+      live[s] = false;
+      HIP_CHECK(hipStreamSynchronize(stream_[s]));
+      const mp::Batch& b = plan[s];
+      for (size_t j = 0; j < b.order.size(); ++j)  // sorted position -> (file, piece) order
+        memcpy(nodes + (b.first_unit + b.order[j]) * 32, h_dig_[s] + j * 32, 32);
+    };
+    try {
+      for (int s = 0;; s ^= 1) {
+        drain(s);  // slot s free again (its previous batch has completed)
+        if (!planner.next(plan[s])) break;
+        const mp::Batch& b = plan[s];
+        fill_batch(files, b, s, readable ? readable + b.first_unit : nullptr);
+        const int64_t nl = (int64_t)b.leaves.size(), nu = (int64_t)b.units.size();
+        memcpy(h_tab_[s], b.leaves.data(), (size_t)nl * sizeof(PlanLeaf));
+        hipStream_t st = stream_[s];
+        HIP_CHECK(hipMemcpyAsync(d_buf_[s], h_buf_[s], (size_t)b.data_bytes,
+                                 hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_tab_[s], h_tab_[s], (size_t)nl * sizeof(PlanLeaf),
+                                 hipMemcpyHostToDevice, st));
+        if (nl < b.width_sum)  // missing leaves: 32 zero bytes each
+          HIP_CHECK(hipMemsetAsync(d_dig_[s][0], 0, (size_t)b.width_sum * 32, st));
+        launch_leaf_table(st, d_buf_[s], d_tab_[s], nl, d_dig_[s][0]);
+        if (b.w1_count)  // width-1 units: their leaf is their node, the tail of both orders
+          HIP_CHECK(hipMemcpyAsync(d_res_[s] + (nu - b.w1_count) * 32,
+                                   d_dig_[s][0] + (b.width_sum - b.w1_count) * 32,
+                                   (size_t)b.w1_count * 32, hipMemcpyDeviceToDevice, st));
+        int cur = 0;
+        for (const mp::Level& lv : b.levels) {
+          launch_pairs_fin(st, d_dig_[s][cur], lv, d_dig_[s][cur ^ 1], d_res_[s]);
+          cur ^= 1;
+        }
+        HIP_CHECK(hipMemcpyAsync(h_dig_[s], d_res_[s], (size_t)nu * 32, hipMemcpyDeviceToHost, st));
+        live[s] = true;
+      }
+      drain(0);
+      drain(1);
+    } catch (...) {
+      // nothing of this call stays in flight on the slots the next call reuses
+      for (int s = 0; s < 2; ++s)
+        if (hipStreamSynchronize(stream_[s]) != hipSuccess) (void)hipGetLastError();
+      throw;
     }
   }
 
@@ -665,6 +891,9 @@ class MerkleHasher {
   uint8_t* d_buf_[2] = {nullptr, nullptr};
   uint8_t* h_dig_[2] = {nullptr, nullptr};
   uint8_t* d_dig_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  PlanLeaf* h_tab_[2] = {nullptr, nullptr};  // see ensure_plan_buffers
+  PlanLeaf* d_tab_[2] = {nullptr, nullptr};
+  uint8_t* d_res_[2] = {nullptr, nullptr};
   std::vector<Digest> pads_;
 };
 
@@ -688,6 +917,12 @@ void require_piece_len(const MerkleHasher& h, int64_t piece_len) {
     throw std::invalid_argument("piece_len must be a power of two, at least 16384");
   if (piece_len > h.batch_bytes())
     throw std::invalid_argument("piece_len exceeds the hasher's batch_bytes");
+}
+
+void require_files(const FileList& files) {
+  if (files.empty()) throw std::invalid_argument("files must not be empty");
+  for (const auto& f : files)
+    if (f.second <= 0) throw std::invalid_argument("length must be > 0");
 }
 
 py::tuple tree_tuple(const Tree& t) { return py::make_tuple(py::bytes(t.layer), py::bytes(t.root)); }
@@ -812,6 +1047,42 @@ PYBIND11_MODULE(_gpumerkle, m) {
           py::arg("path"), py::arg("length"), py::arg("piece_len"), py::arg("expected"),
           "One byte per piece (1 = good) against the piece layer, or against the pieces root for "
           "a file no larger than a piece; pieces a missing or short file cannot cover are 0")
+      .def(
+          "hash_files",
+          [](MerkleHasher& h, const FileList& files, int64_t piece_len) {
+            require_piece_len(h, piece_len);
+            require_files(files);
+            std::string out;
+            {
+              py::gil_scoped_release rel;
+              out = h.hash_files(files, piece_len);
+            }
+            return py::bytes(out);
+          },
+          py::arg("files"), py::arg("piece_len"),
+          "32 bytes per unit of `files` [(path, length)], file order then piece order: the piece "
+          "layer of a file longer than a piece, the pieces root of a smaller one. Pieces of many "
+          "files share a device batch")
+      .def(
+          "verify_files",
+          [](MerkleHasher& h, const FileList& files, int64_t piece_len, const py::bytes& expected) {
+            require_piece_len(h, piece_len);
+            require_files(files);
+            std::string ex = expected;
+            if ((int64_t)ex.size() != MerkleHasher::total_units(files, piece_len) * 32)
+              throw std::invalid_argument(
+                  "expected must hold, per file in order, the piece layer or the 32-byte root of "
+                  "a file no larger than a piece");
+            std::vector<uint8_t> ok;
+            {
+              py::gil_scoped_release rel;
+              ok = h.verify_files(files, piece_len, ex);
+            }
+            return py::bytes((const char*)ok.data(), ok.size());
+          },
+          py::arg("files"), py::arg("piece_len"), py::arg("expected"),
+          "One byte per unit (1 = good) in the order of hash_files; units a missing or short file "
+          "cannot cover are 0")
       .def(
           "kernel_bench",
           [](MerkleHasher& h, int64_t n_leaves, int iters) {

@@ -10,6 +10,7 @@
 #include <netinet/tcp.h>
 #include <sys/socket.h>
 
+#include "merkle_plan.h"
 #include "native.h"
 
 namespace py = pybind11;
@@ -561,6 +562,40 @@ PYBIND11_MODULE(_native, m) {
         return l;
       },
       py::arg("path"), py::arg("ranges"), py::arg("algo"), py::arg("threads") = 0);
+  m.def(
+      "merkle_plan",
+      [](const std::vector<int64_t>& lengths, int64_t piece_len, int64_t batch_bytes) {
+        namespace mp = stager::merkle_plan;
+        mp::Planner planner(lengths, piece_len, batch_bytes);
+        py::list out;
+        for (mp::Batch b; planner.next(b);) {
+          py::list units, leaves, reads, levels;
+          for (const mp::Unit& u : b.units)
+            units.append(py::make_tuple(u.file, u.piece, u.width, u.slot_off, u.bytes));
+          for (const mp::Leaf& l : b.leaves) leaves.append(py::make_tuple(l.src, l.len, l.dst));
+          for (const mp::Read& r : b.reads)
+            reads.append(py::make_tuple(r.file, r.file_off, r.len, r.slot_off));
+          for (const mp::Level& l : b.levels)
+            levels.append(py::make_tuple(l.n_pairs, l.fin_start, l.unit_base));
+          py::dict d;
+          d["first_unit"] = b.first_unit;
+          d["data_bytes"] = b.data_bytes;
+          d["width_sum"] = b.width_sum;
+          d["w1_count"] = b.w1_count;
+          d["units"] = units;
+          d["leaves"] = leaves;
+          d["reads"] = reads;
+          d["levels"] = levels;
+          d["order"] = py::cast(b.order);
+          out.append(d);
+        }
+        return out;
+      },
+      py::arg("lengths"), py::arg("piece_len"), py::arg("batch_bytes"),
+      "Batches of the BEP 52 device recheck (csrc/merkle_plan.h) as plain data: per batch "
+      "units (file, piece, width, slot_off, bytes) in file order, leaves (src, len, dst), reads "
+      "(file, file_off, len, slot_off), levels (n_pairs, fin_start, unit_base) and order (sorted "
+      "position -> unit index)");
 
   py::class_<Hasher>(m, "Hasher")
       .def(py::init<const std::string&>())

@@ -66,7 +66,7 @@ def build_native(force: bool = False, verbose: bool = True) -> Path:
             CSRC / "tls.cpp", CSRC / "peerwire.cpp"]
     out = OPS / f"_native{EXT}"
     if force or _stale(out, srcs + [CSRC / "native.h", CSRC / "crc32c.h",
-                                    CSRC / "gpu_part_api.h"]):
+                                    CSRC / "gpu_part_api.h", CSRC / "merkle_plan.h"]):
         cxx = os.environ.get("CXX", "g++")
         cmd = [cxx, "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden",
                "-march=x86-64-v3", "-Wall", "-Wno-unused-result",
@@ -91,7 +91,7 @@ def build_gpumerkle(force: bool = False, verbose: bool = True) -> Path:
     """BEP 52 SHA-256 merkle kernels (csrc/gpu_sha256_merkle.hip): a module of its own."""
     srcs = [CSRC / "gpu_sha256_merkle.hip"]
     out = OPS / f"_gpumerkle{EXT}"
-    if force or _stale(out, srcs):
+    if force or _stale(out, srcs + [CSRC / "merkle_plan.h"]):
         hipcc = str(ROCM / "bin" / "hipcc")
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
                "-fvisibility=hidden", *_pybind_includes(), str(srcs[0]), "-o", str(out)]
